@@ -34,6 +34,23 @@ in-process loopback transport whose all-reduce is captured into the step's
 HIP graph (parallel/loop.py WorldGraph): a rehearsal of the N > 1 timed path
 (bucket all-reduces forked onto the comm stream inside the captured step) on
 a single-GPU box -- its throughput is not a scaling number.
+
+A plain run only sets up, warms up, times the K steps and prints the record.
+``--full`` adds the side measurement that needs a run of its own: the
+PS-parity microbenchmark (ResNet models), appended to the record as
+``ps_parity``.  ``--dump-outputs DIR`` writes what the last timed step
+returned (logits and loss) as ``DIR/<name>.npy`` for output-for-output
+comparison of two builds: inputs and initial weights depend only on the
+arguments.  The default kernels are not reproducible from run to run (BatchNorm
+statistics and split weight gradients are summed with atomics; bf16 layers
+amplify the order noise to about 6 % rms of a ResNet-50 logit within one
+forward), so a dump run uses the ordered reductions of
+``singa_amd.set_deterministic`` (``--deterministic auto``): its outputs are
+bitwise the same every run, its steps far slower (ResNet-50, batch 1024:
+670 ms against 61 ms), its record carries ``config.deterministic: true``
+and its throughput is not the headline figure.  ``--dump-outputs DIR
+--deterministic off`` times and dumps the default kernels instead: headline
+speed, outputs comparable only within that noise.
 """
 from __future__ import annotations
 
@@ -170,6 +187,31 @@ def replica_guard(comm, optimizer, dev) -> dict:
             "bitwise_equal": bool(np.array_equal(hi, lo))}
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: cap on the bytes written, all files of all ranks together
+
+
+def dump_outputs(dirname: str, arrays: dict, rank: int = 0, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Write ``arrays`` (name -> numpy array) as float32/float64
+    ``dirname/<name>.npy`` (ranks > 0: ``<name>.rank<r>.npy``).  An array over
+    its equal share of ``budget`` is stored as a fixed, seeded sample of its
+    flattened elements (same indices for the same shape in every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = budget // max(1, len(arrays)) - 128  # (128: the .npy header)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        path = os.path.join(dirname, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy")
+        np.save(path, a)
+        written[name] = list(a.shape)
+    return written
+
+
 def run_rank(args, rank: int, world: int, local: int, comm, loopback: bool = False):
     """One rank's benchmark; returns (exit code, JSON record or None)."""
     import torch
@@ -183,6 +225,18 @@ def run_rank(args, rank: int, world: int, local: int, comm, loopback: bool = Fal
                                     set_default=not loopback)
     if not loopback:
         dev.SetRandSeed(args.seed + rank)
+    deterministic = (args.deterministic == "on" or (args.deterministic == "auto" and bool(args.dump_outputs))
+                     or os.environ.get("SINGA_AMD_DETERMINISTIC", "0") == "1")
+    if deterministic:
+        # outputs meant for comparison must be the same every run: the default
+        # kernels sum BatchNorm statistics and split weight gradients with
+        # atomics in arbitrary order (bf16 layers amplify that to percents of
+        # a logit), so a dump run takes the ordered, bitwise reproducible ones
+        # unless told otherwise (--deterministic off) -- far slower; the
+        # record says which kernels ran
+        import singa_amd
+
+        singa_amd.set_deterministic(True)
     m, (tx, ty), base_opt, info = _build(args, dev, rank)
     # DistOpt at every N (at N = 1 it is the plain fused update: same path,
     # and the record carries the bucket layout the N > 1 runs exchange)
@@ -250,11 +304,15 @@ def run_rank(args, rank: int, world: int, local: int, comm, loopback: bool = Fal
                 print(f"bench.py: replicas diverged across ranks ({replicas}); no number reported", file=sys.stderr)
             return 4, None
     final_loss = float(G.to_numpy(G.to(loss.data, torch.float32)))
+    if args.dump_outputs and args.steps > 0:
+        # what the last timed step handed back to its caller
+        dump_outputs(args.dump_outputs, {"out": G.to_numpy(out.data), "loss": G.to_numpy(loss.data)}, rank,
+                     budget=DUMP_BUDGET_BYTES // world)
     ps = None
-    if not args.no_ps_parity and not loopback and info["model"].startswith("ResNet"):
-        # the reference's own headline benchmark (PS update+collect of the 12
-        # MLP tensors), measured on the same ranks AFTER the
-        # timed region: it does not touch the images/s number
+    if args.full and not args.no_ps_parity and not loopback and info["model"].startswith("ResNet"):
+        # --full: the reference's own headline benchmark (PS update+collect of
+        # the 12 MLP tensors), measured on the same ranks AFTER
+        # the timed region: it does not touch the images/s number
         from singa_amd.parallel import ps_parity
 
         try:
@@ -304,6 +362,7 @@ def run_rank(args, rank: int, world: int, local: int, comm, loopback: bool = Fal
         "config": {"model": info["model"], "global_batch": world * info["batch"], "seq_len": info["seq_len"],
                    "image": info["image"], "parallelism": f"dp{world}",
                    "exec": "hipgraph" if m.graph_mode else "eager", "optimizer": info["optimizer"],
+                   "deterministic": deterministic,
                    "comm": comm_info, "final_loss": round(final_loss, 4)},
     }
     if loopback:
@@ -349,8 +408,20 @@ def _parser():
     ap.add_argument("--loss-curve", action="store_true", help="record every step's loss (syncs; diagnostics only)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--sync-warmup", action="store_true", help="synchronize after every warmup step (diagnostics)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements that take runs of their own (the PS-parity "
+                         "microbenchmark after the timed region); a plain run only times the steps")
     ap.add_argument("--no-ps-parity", action="store_true",
-                    help="skip the PS-parity microbenchmark appended after the timed region")
+                    help="with --full: skip the PS-parity microbenchmark")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned (out, loss) as DIR/<name>.npy "
+                         "(float32; at most 64 MB, a fixed seeded sample of a larger array). Unless --deterministic off "
+                         "is given, the run uses the deterministic kernels so that the files are the same every run")
+    ap.add_argument("--deterministic", choices=("auto", "on", "off"), default="auto",
+                    help="ordered, atomic-free reductions (singa_amd.set_deterministic): bitwise reproducible steps, "
+                         "about 11x slower for ResNet-50. auto: on with --dump-outputs, else off. With "
+                         "'--dump-outputs DIR --deterministic off' the default (headline) kernels are timed and "
+                         "dumped; their outputs differ from run to run by about 6 %% rms of a logit")
     ap.add_argument("--lr", type=float, default=0.01,
                     help="SGD lr (random labels + no warmup: 0.1 occasionally diverges; throughput is lr-independent)")
     ap.add_argument("--grad-dtype", choices=("fp32", "bf16"), default="fp32",

@@ -156,3 +156,38 @@ def test_replica_guard_detects_drift():
     other = bench.replica_checksums(_StubOpt(w2, opt_.buckets))
     r = bench.replica_guard(_StubComm(other), opt_, cpu)
     assert not r["ok"] and r["max_rel_spread"] > 1e-6
+
+
+def test_plain_run_is_lean_by_default():
+    """--full (the side measurements) is off unless asked for."""
+    bench = _bench()
+    a = bench._parser().parse_args([])
+    assert a.full is False and a.dump_outputs is None and a.deterministic == "auto"
+    a = bench._parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_npy_within_budget(tmp_path):
+    """--dump-outputs: float32/float64 .npy per name; an array over its share
+    of the byte budget is stored as the same seeded sample every time."""
+    import numpy as np
+
+    bench = _bench()
+    rng = np.random.RandomState(1)
+    out = rng.randn(6, 10).astype(np.float32)
+    loss = np.float64(2.5)
+    ids = np.arange(5, dtype=np.int32)
+    w = bench.dump_outputs(str(tmp_path / "a"), {"out": out, "loss": loss, "ids": ids})
+    assert w == {"out": [6, 10], "loss": [], "ids": [5]}
+    got = np.load(tmp_path / "a" / "out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, out)
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    assert np.load(tmp_path / "a" / "ids.npy").dtype == np.float32
+    # budget of 2 x (80 + 128 header) bytes: 20 of the 60 float32 elements of `out` are kept
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"out": out, "loss": loss}, budget=416)
+    b, c = np.load(tmp_path / "b" / "out.npy"), np.load(tmp_path / "c" / "out.npy")
+    assert b.shape == (20,) and np.array_equal(b, c) and set(b.tolist()) <= set(out.reshape(-1).tolist())
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 416
+    bench.dump_outputs(str(tmp_path / "a"), {"out": out}, rank=1)
+    assert (tmp_path / "a" / "out.rank1.npy").exists()

@@ -10,7 +10,8 @@ from singa_amd import autograd
 from singa_amd.config import schema
 from singa_amd.runtime import NeuralNet, Worker
 
-REF = "/root/reference/examples/mnist"
+# the reference's examples/mnist settings files, stored unchanged
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_mnist")
 
 
 def conv_test_net(partition=None):
@@ -37,7 +38,6 @@ def conv_test_net(partition=None):
     return net
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference examples not mounted")
 @pytest.mark.parametrize("f,msg", [("mlp.conf", "ModelProto"), ("conv.conf", "ModelProto"),
                                    ("cluster.conf", "ClusterProto"), ("topology.conf", "Topology")])
 def test_reference_confs_parse_unchanged(f, msg):

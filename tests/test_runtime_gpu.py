@@ -11,7 +11,8 @@ from singa_amd.config import schema
 from singa_amd.runtime import NeuralNet, Worker
 
 pytestmark = pytest.mark.gpu
-REF = "/root/reference/examples/mnist"
+# the reference's examples/mnist settings files, stored unchanged
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_mnist")
 
 LENET = """
 name: "lenet-gpu" train_steps: 60 test_steps: 2 test_frequency: 30 display_frequency: 20
@@ -71,7 +72,6 @@ def test_lenet_gpu_matches_cpu_first_step(gpu):
     assert abs(out[0] - out[1]) < 2e-2 * max(1.0, abs(out[0])), out
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference examples not mounted")
 def test_reference_mlp_conf_steps_on_gpu(gpu):
     from singa_amd.device import create_cuda_gpu
 
